@@ -9,6 +9,20 @@ device memory (partition selection, LUT build, LUT16 scan + top-k, SOAR-free
 dedupe, exact reorder and sort all inside the step).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config glove|sift]
+                    [--dump-outputs DIR] [--full]
+
+A plain run does what the headline figure needs and no more: it builds the
+index, warms up, times the K steps and prints the result line (`value`,
+`ms_per_step` and the configuration).  `--full` adds every other measurement
+and check to the same line: recall@10 against brute force, the QPS-recall
+operating points, the one-batch-at-a-time latency, the per-stage replay and
+the scan's roofline, the other scaling mode at N > 1, parity with the oracle
+and the CPU baseline (each with its own `--no-*` switch).
+
+`--dump-outputs DIR` writes what the last timed step returned to its caller
+(ids, distances and per-query counts of the batch) as DIR/<name>.npy; the
+inputs are seeded, so two builds run with the same arguments can be compared
+array for array.
 
 `--config sift` measures BASELINE.json configs[2] (SIFT1M shape, squared L2,
 2000 leaves) as a secondary line; the default is the metric's configuration.
@@ -368,6 +382,17 @@ def cpu_baseline_restatement(ix, q, gpu_idx, threads):
                 id_mismatch_vs_gpu=float((out[0] != gpu_idx).mean()))
 
 
+def dump_outputs(path, idx, dist, count):
+    """--dump-outputs: the (idx, dist, count) device tensors a caller of the
+    timed step received, as <path>/{idx,dist,count}.npy.  Ids and counts go
+    out as float64 (exact for any uint32 id), distances as the float32 they
+    are."""
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "idx.npy"), idx.cpu().numpy().astype(np.float64))
+    np.save(os.path.join(path, "dist.npy"), dist.cpu().numpy().astype(np.float32))
+    np.save(os.path.join(path, "count.npy"), count.cpu().numpy().astype(np.float64))
+
+
 def launch_plan(gpus, env, argv, port=None):
     """What `bench.py --gpus N` does before touching the GPU:
     ("run", world) -- run as one rank of `world` (WORLD_SIZE, or 1);
@@ -409,6 +434,11 @@ def main():
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--n", type=int, default=1_183_514)
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline figure: recall, operating points, latency, stages "
+                         "and roofline, the other scaling mode, oracle parity, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's results as DIR/{idx,dist,count}.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-threads", type=int, default=0)
     ap.add_argument("--config", choices=sorted(CONFIGS), default="glove")
@@ -537,17 +567,22 @@ def main():
     # it nears ms_per_step the host, not the device, sets the rate
     issue_ms = enqueue_s[n_fl] * 1000.0 / args.steps
     value = world * NQ * args.steps / elapsed
-    # the same in-flight steps again with two HIP events around every scan
-    # launch on its own stream (profiling mode 2: no synchronisation, the
-    # batches stay in flight): the roofline's per-launch scan duration, and
-    # the rate with the events (their host cost is kept out of `value`)
-    nat.set_profiling(2)
-    elapsed_ev = timed_steps(n_fl)
-    t_fl = nat.timings()
-    nat.set_profiling(False)
-    scan_ms_fl, scan_launches = float(t_fl["scan_ms_mode2"]), int(t_fl["scan_launches"])
+    # what the last timed step returned (the later passes reuse its buffers)
+    last_out = None
+    if args.dump_outputs:
+        last_out = [t.clone() for t in outs[(args.steps - 1) % n_fl]]
+    if args.full:
+        # the same in-flight steps again with two HIP events around every scan
+        # launch on its own stream (profiling mode 2: no synchronisation, the
+        # batches stay in flight): the roofline's per-launch scan duration, and
+        # the rate with the events (their host cost is kept out of `value`)
+        nat.set_profiling(2)
+        elapsed_ev = timed_steps(n_fl)
+        t_fl = nat.timings()
+        nat.set_profiling(False)
+        scan_ms_fl, scan_launches = float(t_fl["scan_ms_mode2"]), int(t_fl["scan_launches"])
     # the same steps one at a time (one stream): the per-batch latency
-    elapsed_1 = timed_steps(1) if n_fl > 1 and not args.no_latency else None
+    elapsed_1 = timed_steps(1) if args.full and n_fl > 1 and not args.no_latency else None
 
     # strong scaling: rank 0's 1000-query batch split over
     # the ranks by query_slice (SearchBatchedParallel's chunking,
@@ -555,7 +590,7 @@ def main():
     # stream and the slices' results all-gathered (RCCL), so every rank holds
     # the whole batch's results; QPS = 1000 x K / max-rank time
     strong = None
-    if world > 1 or args.scaling == "strong":
+    if args.scaling == "strong" or (args.full and world > 1):
         from scann_amd.distributed import SplitBatchSearcher, query_slice
         q0d = qd if rank == 0 else torch.from_numpy(queries_for_rank(db.shape[1], 0)).to(dev)
         b0, e0_ = query_slice(NQ, rank, world)
@@ -582,6 +617,8 @@ def main():
             strong_step(i)
         el_s = timed_steps(n_fl, strong_step)
         torch.cuda.synchronize()
+        if args.dump_outputs and args.scaling == "strong":
+            last_out = [t.clone() for t in gathered[(args.steps - 1) % n_fl]]
         strong = {"qps": round(NQ * args.steps / el_s, 1),
                   "ms_per_step": round(el_s * 1000.0 / args.steps, 4),
                   "queries_per_gpu": e0_ - b0,
@@ -598,6 +635,62 @@ def main():
             g = gathered[(args.steps - 1) % n_fl]
             whole = outs[(args.steps - 1) % n_fl] if args.steps else outs[0]
             strong["ids_equal_whole_batch"] = bool(torch.equal(g[0], whole[0]))
+
+    # the headline figure and what it was measured on: a plain run's whole line
+    result = {
+        "metric": CFG["metric_name"],
+        "value": round(value, 1),
+        "unit": "queries/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(ms_per_step, 4),
+        "in_flight": n_fl,
+        "host_issue_ms_per_step": round(issue_ms, 4),
+        "timing": "HIP events between the timed region's barrier + synchronize brackets "
+                  "(max over ranks); wall clock of the same brackets: "
+                  f"{wall_ms_per_step:.4f} ms/step",
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "int8",
+        "data": CFG["data"],
+        "config": {
+            "workload": CFG["workload"],
+            "num_datapoints": int(args.n), "dim": int(db.shape[1]), "num_leaves": LEAVES,
+            "leaves_to_search": LEAVES_TO_SEARCH, "pre_reorder_nn": PRE_NN,
+            "final_nn": FINAL_NN, "batch": NQ,
+            "parallelism": f"query-sharded replicas x{world}, {n_fl} batches in flight per GPU",
+        },
+    }
+    if strong is not None:
+        if args.scaling == "strong":
+            # the split batch is the line's value; the weak figures beside it
+            result["weak_scaling"] = {"qps": result["value"],
+                                      "ms_per_step": result["ms_per_step"],
+                                      "parallelism": result["config"]["parallelism"]}
+            result["value"] = strong["qps"]
+            result["ms_per_step"] = strong["ms_per_step"]
+            result["scaling"] = "strong"
+            result["config"]["batch"] = NQ
+            result["config"]["parallelism"] = strong["parallelism"]
+            result["strong_scaling"] = {k: v for k, v in strong.items()
+                                        if k not in ("qps", "ms_per_step", "parallelism")}
+        else:
+            result["strong_scaling"] = strong
+    if last_out is not None and rank == 0:
+        dump_outputs(args.dump_outputs, *last_out)
+
+    def finish():
+        if rank == 0:
+            print(json.dumps(result), flush=True)
+        nat.close()
+        if dist is not None:
+            dist.barrier()
+            dist.destroy_process_group()
+
+    if not args.full:
+        return finish()
 
     # per-stage durations, each kernel alone: the same steps replayed one at
     # a time with HIP events recorded on the call's stream around every stage
@@ -670,34 +763,10 @@ def main():
     traffic = scan_traffic(args.config)
 
     if rank == 0:
-        result = {
-            "metric": CFG["metric_name"],
-            "value": round(value, 1),
-            "unit": "queries/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(ms_per_step, 4),
-            "in_flight": n_fl,
-            "host_issue_ms_per_step": round(issue_ms, 4),
+        result.update({
             "single_stream": ({"qps": round(world * NQ * args.steps / elapsed_1, 1),
                                "ms_per_step": round(elapsed_1 * 1000.0 / args.steps, 4)}
                               if elapsed_1 else None),
-            "timing": "HIP events between the timed region's barrier + synchronize brackets "
-                      "(max over ranks); wall clock of the same brackets: "
-                      f"{wall_ms_per_step:.4f} ms/step",
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "int8",
-            "data": CFG["data"],
-            "config": {
-                "workload": CFG["workload"],
-                "num_datapoints": int(args.n), "dim": int(db.shape[1]), "num_leaves": LEAVES,
-                "leaves_to_search": LEAVES_TO_SEARCH, "pre_reorder_nn": PRE_NN,
-                "final_nn": FINAL_NN, "batch": NQ,
-                "parallelism": f"query-sharded replicas x{world}, {n_fl} batches in flight per GPU",
-            },
             "recall_at_10": round(recall, 4),
             "roofline": dict(roof, traffic=traffic,
                              hbm_GBps_measured=(round(traffic / (avg_scan_ms * 1e-3) / 1e9, 1)
@@ -714,22 +783,7 @@ def main():
                                         for p in points if p["recall_at_10"] >= 0.95), None),
             "candidates_max": t_last["max_candidates"],
             "candidates_mean": round(float(t_last["mean_candidates"]), 1),
-        }
-        if strong is not None:
-            if args.scaling == "strong":
-                # the split batch is the line's value; the weak figures beside it
-                result["weak_scaling"] = {"qps": result["value"],
-                                          "ms_per_step": result["ms_per_step"],
-                                          "parallelism": result["config"]["parallelism"]}
-                result["value"] = strong["qps"]
-                result["ms_per_step"] = strong["ms_per_step"]
-                result["scaling"] = "strong"
-                result["config"]["batch"] = NQ
-                result["config"]["parallelism"] = strong["parallelism"]
-                result["strong_scaling"] = {k: v for k, v in strong.items()
-                                            if k not in ("qps", "ms_per_step", "parallelism")}
-            else:
-                result["strong_scaling"] = strong
+        })
         # full-size parity: oracle (ideal mode) on a query subset, ids must match
         from oracle import binding as oracle
         oracle.build()
@@ -747,11 +801,7 @@ def main():
             log(f"cpu baseline with {threads} threads ...")
             result["cpu_baseline"] = cpu_baseline(ix, q, out_idx.cpu().numpy().astype(np.uint32),
                                                   threads)
-        print(json.dumps(result), flush=True)
-    nat.close()
-    if dist is not None:
-        dist.barrier()
-        dist.destroy_process_group()
+    finish()
 
 
 def main_generated(args, rank, world, local, dist, dev):
@@ -847,12 +897,48 @@ def main_generated(args, rank, world, local, dist, dev):
     for _ in range(args.warmup):
         step()
     elapsed = timed(step, args.steps)
+    ms_per_step = elapsed * 1000.0 / args.steps
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, *res["out"])
+    nat = eng.nat
+    # the headline figure and what it was measured on: a plain run's whole line
+    result = {
+        "metric": CFG["metric_name"],
+        # the ranks search the same batch jointly: whole-job QPS
+        "value": round(NQ * args.steps / elapsed, 1),
+        "unit": "queries/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": round(ms_per_step, 4), "in_flight": n_fl, "higher_is_better": True,
+        "scaling": "strong",
+        "vs_baseline": None, "dtype": "int8", "data": CFG["data"],
+        "config": {"workload": CFG["workload"], "num_datapoints": n, "dim": CFG["dim"],
+                   "num_leaves": LEAVES, "leaves_to_search": LEAVES_TO_SEARCH,
+                   "pre_reorder_nn": PRE_NN, "final_nn": FINAL_NN, "batch": NQ,
+                   "split": split, "shard_members": int(ix.num_members),
+                   "parallelism": (f"range split x{split}" if world == split else
+                                   f"rank 0 of a {split}-way range split on 1 GPU, "
+                                   f"{n_fl} batches in flight")},
+        "build_s": round(build_s, 2),
+        "build": ("generation + the whole shard build on this GPU in the HIP build kernels "
+                  "(k-means on a %d-row sample, tokenization%s, grouping, codebook, codes)"
+                  % (CFG.get("train_sample", max(250_000, 20 * LEAVES)),
+                     " + SOAR" if CFG["soar"] else "")),
+    }
+
+    def finish():
+        if rank == 0:
+            print(json.dumps(result), flush=True)
+        nat.close()
+        if dist is not None:
+            dist.barrier()
+            dist.destroy_process_group()
+
+    if not args.full:
+        return finish()
+
     search_s = timed(search, args.steps)
     merge_s = timed(merge, args.steps)
-    ms_per_step = elapsed * 1000.0 / args.steps
     # recall@10 of rank 0's merged result against exact brute force over the
     # rows the split's ranks hold (world == 1: this shard's rows)
-    nat = eng.nat
     nat.set_profiling(True)
     search()
     scan_ms, scan_bytes = [], []
@@ -910,21 +996,7 @@ def main_generated(args, rank, world, local, dist, dev):
     roof = scan_roofline(bytes_per_launch, avg_scan_ms, stages, ix.num_blocks)
     traffic = scan_traffic(args.config)
     if rank == 0:
-        result = {
-            "metric": CFG["metric_name"],
-            # the ranks search the same batch jointly: whole-job QPS
-            "value": round(NQ * args.steps / elapsed, 1),
-            "unit": "queries/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(ms_per_step, 4), "in_flight": n_fl, "higher_is_better": True,
-            "scaling": "strong",
-            "vs_baseline": None, "dtype": "int8", "data": CFG["data"],
-            "config": {"workload": CFG["workload"], "num_datapoints": n, "dim": CFG["dim"],
-                       "num_leaves": LEAVES, "leaves_to_search": LEAVES_TO_SEARCH,
-                       "pre_reorder_nn": PRE_NN, "final_nn": FINAL_NN, "batch": NQ,
-                       "split": split, "shard_members": int(ix.num_members),
-                       "parallelism": (f"range split x{split}" if world == split else
-                                       f"rank 0 of a {split}-way range split on 1 GPU, "
-                                       f"{n_fl} batches in flight")},
+        result.update({
             "recall_at_10": round(recall, 4),
             "recall_reference": ("exact brute force over the shard's rows" if world == 1
                                  else "exact brute force over the whole dataset"),
@@ -934,11 +1006,6 @@ def main_generated(args, rank, world, local, dist, dev):
                                         "recall_at_10": p["recall_at_10"]}
                                        for p in points if p["recall_at_10"] >= 0.95),
                                       key=lambda p: p["qps"], default=None),
-            "build_s": round(build_s, 2),
-            "build": ("generation + the whole shard build on this GPU in the HIP build kernels "
-                      "(k-means on a %d-row sample, tokenization%s, grouping, codebook, codes)"
-                      % (CFG.get("train_sample", max(250_000, 20 * LEAVES)),
-                         " + SOAR" if CFG["soar"] else "")),
             "shard_search_ms": round(search_s * 1000.0 / args.steps, 4),
             "merge_ms": round(merge_s * 1000.0 / args.steps, 4),
             "merge_input": (f"all-gather of {split} ranks" if world == split else
@@ -953,7 +1020,7 @@ def main_generated(args, rank, world, local, dist, dev):
             "stage_ms": {k2: round(stages[k2], 4) for k2 in
                          ("partition_ms", "invert_ms", "seed_scan_ms", "scan_ms", "select_ms",
                           "total_ms")},
-        }
+        })
         view_ids = None
         if not args.no_parity:
             result["parity_vs_oracle"], view_ids = shard_parity(
@@ -961,11 +1028,7 @@ def main_generated(args, rank, world, local, dist, dev):
         if not args.no_cpu_baseline:
             result["cpu_baseline"] = cpu_baseline_shard(ix, q, args.cpu_threads or host_threads()[0],
                                                         view_ids)
-        print(json.dumps(result), flush=True)
-    nat.close()
-    if dist is not None:
-        dist.barrier()
-        dist.destroy_process_group()
+    finish()
 
 
 def _generated_truth(ds, q, r0, r1, dev):

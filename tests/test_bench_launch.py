@@ -48,6 +48,24 @@ def test_peek_gpus_ignores_other_flags():
     assert bench._peek_gpus([]) == 1
 
 
+def test_dump_outputs_writes_float_arrays(tmp_path):
+    """--dump-outputs: one .npy per result array, float32 / float64 only, ids
+    exact up to the uint32 range."""
+    import numpy as np
+    import torch
+    idx = torch.tensor([[0, 1_183_513], [2**31 - 1, 7]], dtype=torch.int32)
+    dist = torch.tensor([[-0.5, 0.25], [1e-30, 3.0]], dtype=torch.float32)
+    cnt = torch.tensor([2, 1], dtype=torch.int32)
+    out = tmp_path / "dump"
+    bench.dump_outputs(str(out), idx, dist, cnt)
+    assert sorted(os.listdir(out)) == ["count.npy", "dist.npy", "idx.npy"]
+    got = {n: np.load(out / f"{n}.npy") for n in ("idx", "dist", "count")}
+    assert got["idx"].dtype == np.float64 and got["count"].dtype == np.float64
+    assert got["dist"].dtype == np.float32
+    assert np.array_equal(got["idx"], idx.numpy()) and np.array_equal(got["count"], cnt.numpy())
+    assert np.array_equal(got["dist"].view(np.uint32), dist.numpy().view(np.uint32))
+
+
 def test_mismatch_exits_nonzero_before_gpu():
     env = dict(os.environ, WORLD_SIZE="3", RANK="0", LOCAL_RANK="0")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2"], env=env,

@@ -11,7 +11,7 @@ step() { echo "[ab_env] $(date +%T) $*" >&2; }
 for rep in 1 2; do
   for E in ${ENVS:-SMX_NARROW=1}; do
     step "$E rep $rep" &&
-    env ${E//,/ } timeout -k 10 ${LIMIT:-240} python3 bench.py --steps ${STEPS:-200} --warmup 10 \
+    env ${E//,/ } timeout -k 10 ${LIMIT:-240} python3 bench.py --full --steps ${STEPS:-200} --warmup 10 \
         --no-cpu-baseline --no-sweep ${BENCH_ARGS:-} >> $O/$E.json 2>> $O/bench.err || exit 1
   done
 done

@@ -15,7 +15,7 @@ for rep in $(seq ${REPS:-2}); do
     n=$(basename $L .so)
     for C in ${CFGS:-glove}; do
       step "$C $n rep $rep" &&
-      SMX_LIB=$L timeout -k 10 ${LIMIT:-400} python3 bench.py --config $C --steps ${STEPS:-200} --warmup 20 \
+      SMX_LIB=$L timeout -k 10 ${LIMIT:-400} python3 bench.py --full --config $C --steps ${STEPS:-200} --warmup 20 \
           --no-cpu-baseline --no-sweep --no-parity ${BENCH_ARGS:-} >> $O/$C.$n.json 2>> $O/bench.err || exit 1
     done
   done

@@ -8,7 +8,7 @@ mkdir -p $O
 for rep in $(seq 1 ${REPS:-2}); do
   for L in ${LS:-100 15}; do
     for C in ${CHUNKS:-12 16 20 28 40}; do
-      SMX_CHUNK_TILES=$C timeout -k 10 300 python bench.py --no-cpu-baseline --no-sweep \
+      SMX_CHUNK_TILES=$C timeout -k 10 300 python bench.py --full --no-cpu-baseline --no-sweep \
         --steps ${STEPS:-100} --warmup 20 --leaves-to-search $L \
         > $O/L${L}_chunk${C}_r${rep}.json 2> /dev/null || exit 1
     done

@@ -1,5 +1,5 @@
 """Turn a rocprofv3 --pmc FETCH_SIZE counter collection into
-profiles/scan_traffic_<config>.json (bench.py --config <config>).
+profiles/scan_traffic_<config>.json (bench.py --full --config <config>).
 
     python tools/pmc_traffic.py gpurun_out/pmc1/run_counter_collection.csv [config]
 

@@ -8,7 +8,7 @@ for rep in $(seq ${REPS:-3}); do
   for P in ${PRIOS:-none -1,0,0}; do
     for S in 20 200; do
       if [ "$P" = none ]; then E=""; else E="$P"; fi
-      SMX_BENCH_STREAM_PRIORITY="$E" timeout -k 10 300 python3 bench.py --steps $S --warmup 5 \
+      SMX_BENCH_STREAM_PRIORITY="$E" timeout -k 10 300 python3 bench.py --full --steps $S --warmup 5 \
         --no-cpu-baseline --no-sweep --no-parity --no-latency >> $O/p${P}_s$S.json 2>> $O/err.log || exit 1
     done
   done

@@ -11,7 +11,7 @@ ROOT=$(pwd)
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
 timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$ROOT/$OUT/trace" -o run \
-  -- python3 "$ROOT/bench.py" --no-cpu-baseline --no-sweep --no-parity --in-flight 1 --steps 50 \
+  -- python3 "$ROOT/bench.py" --full --no-cpu-baseline --no-sweep --no-parity --in-flight 1 --steps 50 \
   ${BENCH_ARGS:-} > "$ROOT/$OUT/bench.json" 2> "$ROOT/$OUT/bench.err"
 cd "$ROOT"
 python tools/kstats_summary.py "$OUT/trace/run_kernel_stats.csv" > "$OUT/kernel_summary.txt"

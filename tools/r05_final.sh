@@ -16,6 +16,6 @@ cp profiles/scan_traffic_glove.json profiles/scan_traffic_sift.json $O/ &&
 python tools/trace_overlap.py $O/prof_glove/trace/run_kernel_trace.csv > $O/prof_glove/overlap.txt &&
 python tools/trace_overlap.py $O/prof_sift/trace/run_kernel_trace.csv > $O/prof_sift/overlap.txt &&
 rm -f $O/prof_glove/trace/run_kernel_trace.csv $O/prof_sift/trace/run_kernel_trace.csv &&
-step glove && timeout -k 10 600 python bench.py > $O/bench_glove.json 2> $O/bench_glove.err &&
-step sift && timeout -k 10 600 python bench.py --config sift > $O/bench_sift.json 2> $O/bench_sift.err &&
+step glove && timeout -k 10 600 python bench.py --full > $O/bench_glove.json 2> $O/bench_glove.err &&
+step sift && timeout -k 10 600 python bench.py --full --config sift > $O/bench_sift.json 2> $O/bench_sift.err &&
 step done

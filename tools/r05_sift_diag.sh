@@ -10,5 +10,5 @@ step diag && SMX_LIB=scann_amd/lib/libscann_mi355x_diag.so timeout -k 10 600 pyt
 step prof_sift && BENCH_ARGS="--config sift" timeout -k 10 900 bash tools/profile_bench.sh $O/prof_sift &&
 step traffic && python tools/pmc_traffic.py $O/prof_sift/pmc1/run_counter_collection.csv sift > $O/traffic.log &&
 cp profiles/scan_traffic_sift.json $O/scan_traffic_sift.json &&
-step sift && timeout -k 10 600 python bench.py --config sift > $O/bench_sift.json 2> $O/bench_sift.err &&
+step sift && timeout -k 10 600 python bench.py --full --config sift > $O/bench_sift.json 2> $O/bench_sift.err &&
 step done

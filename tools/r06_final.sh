@@ -15,7 +15,7 @@ mkdir -p $O
 step() { echo "[r06_final] $(date +%T) $*" >&2; }
 fetch() {   # <config>
   (cd /tmp && export TMPDIR=/tmp && timeout -s KILL 500 rocprofv3 --pmc FETCH_SIZE --output-format csv \
-    -d "$ROOT/$O/pmc_$1" -o run --kernel-include-regex "lut16_scan_kernel" -- python3 "$ROOT/bench.py" \
+    -d "$ROOT/$O/pmc_$1" -o run --kernel-include-regex "lut16_scan_kernel" -- python3 "$ROOT/bench.py" --full \
     --config $1 --no-cpu-baseline --no-sweep --no-parity --no-latency --steps 20 > "$ROOT/$O/pmc_$1.log" 2>&1) &&
   python tools/pmc_traffic.py $O/pmc_$1/run_counter_collection.csv $1 > $O/traffic_$1.log &&
   cp profiles/scan_traffic_$1.json $O/ && rm -rf $O/pmc_$1
@@ -33,14 +33,14 @@ a)
   step diag_tests && SMX_LIB=scann_amd/lib/libscann_mi355x_diag.so timeout -k 10 900 python -u -m pytest tests -m gpu -q --timeout 900 --timeout-method thread > $O/diag_tests.log 2>&1 &&
   step done ;;
 b)
-  step glove && timeout -k 10 600 python bench.py > $O/bench_glove.json 2> $O/bench_glove.err &&
-  step glove_s20 && timeout -k 10 600 python bench.py --steps 20 --warmup 5 > $O/bench_glove_s20.json 2> $O/bench_glove_s20.err &&
-  step strong && timeout -k 10 600 python bench.py --no-cpu-baseline --scaling strong > $O/bench_glove_strong.json 2> $O/bench_glove_strong.err &&
-  step sift && timeout -k 10 600 python bench.py --config sift > $O/bench_sift.json 2> $O/bench_sift.err && step done ;;
+  step glove && timeout -k 10 600 python bench.py --full > $O/bench_glove.json 2> $O/bench_glove.err &&
+  step glove_s20 && timeout -k 10 600 python bench.py --full --steps 20 --warmup 5 > $O/bench_glove_s20.json 2> $O/bench_glove_s20.err &&
+  step strong && timeout -k 10 600 python bench.py --full --no-cpu-baseline --scaling strong > $O/bench_glove_strong.json 2> $O/bench_glove_strong.err &&
+  step sift && timeout -k 10 600 python bench.py --full --config sift > $O/bench_sift.json 2> $O/bench_sift.err && step done ;;
 c)
   step fetch_soar && fetch soar100m && step fetch_deep1b && fetch deep1b &&
-  step soar && timeout -k 10 900 python bench.py --config soar100m > $O/bench_soar100m_shard.json 2> $O/bench_soar100m_shard.err &&
-  step deep1b && timeout -k 10 1000 python bench.py --config deep1b > $O/bench_deep1b_shard.json 2> $O/bench_deep1b_shard.err && step done ;;
+  step soar && timeout -k 10 900 python bench.py --full --config soar100m > $O/bench_soar100m_shard.json 2> $O/bench_soar100m_shard.err &&
+  step deep1b && timeout -k 10 1000 python bench.py --full --config deep1b > $O/bench_deep1b_shard.json 2> $O/bench_deep1b_shard.err && step done ;;
 d)
   step alone_deep1b && alone deep1b &&
   step stamps && timeout -k 10 300 python tools/phase_stamps.py 4 > $O/phases_glove.log 2>&1 &&

@@ -8,7 +8,7 @@ mkdir -p $O
 for rep in $(seq 1 ${REPS:-1}); do
 for L in ${LS:-20 100}; do
   for R in ${ROWS:-1024 2048 4096}; do
-    SMX_SEED_ROWS=$R timeout -k 10 300 python bench.py --no-cpu-baseline --no-sweep \
+    SMX_SEED_ROWS=$R timeout -k 10 300 python bench.py --full --no-cpu-baseline --no-sweep \
       --steps ${STEPS:-200} --warmup ${WARMUP:-20} --leaves-to-search $L \
       > $O/L${L}_rows${R}_r${rep}.json 2> $O/L${L}_rows${R}_r${rep}.err || exit 1
   done

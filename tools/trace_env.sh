@@ -11,7 +11,7 @@ for E in ${ENVS:-SMX_NARROW=1}; do
   echo "[trace_env] $(date +%T) $E" >&2
   mkdir -p "$O/$E"
   (export ${E//,/ }; export SMX_LIB=${SMX_LIB:+$ROOT/$SMX_LIB}; timeout -k 10 ${LIMIT:-300} rocprofv3 --kernel-trace --stats --output-format csv \
-      -d "$O/$E" -o run -- python3 "$ROOT/bench.py" --no-cpu-baseline --no-sweep --no-parity \
+      -d "$O/$E" -o run -- python3 "$ROOT/bench.py" --full --no-cpu-baseline --no-sweep --no-parity \
       --steps ${STEPS:-50} ${BENCH_ARGS:-} > "$O/$E/bench.json" 2> "$O/$E/bench.err") || exit 1
 done
 echo "[trace_env] done" >&2
