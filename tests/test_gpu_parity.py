@@ -276,6 +276,7 @@ def test_large_kprime_block_select(native, oracle, small_dot, pre_nn):
     oi, od, oc = oracle.search(ix, q, 24, pre_nn, 10, True, oracle.MODE_IDEAL)
     np.testing.assert_array_equal(gi, oi)
     np.testing.assert_allclose(gd, od, rtol=RTOL)
+    np.testing.assert_array_equal(gd.view(np.uint32), od.view(np.uint32))
 
 
 def test_overflow_rescan_in_block_select(native, oracle, small_dot):
@@ -311,6 +312,7 @@ def test_device_entry_point_is_stream_ordered(native, oracle, small_dot):
     for oi_, od_ in outs:
         np.testing.assert_array_equal(oi_.cpu().numpy().view(np.uint32), oi)
         np.testing.assert_allclose(od_.cpu().numpy(), od, rtol=RTOL)
+        np.testing.assert_array_equal(od_.cpu().numpy().view(np.uint32), od.view(np.uint32))
 
 
 @pytest.mark.parametrize("fix", ["small_dot", "small_l2"])
