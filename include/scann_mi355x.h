@@ -336,6 +336,77 @@ int smx_gather_residuals(const float* d_x, int32_t d, const uint32_t* d_rows,
                          const int32_t* d_leaf, const float* d_centers, int64_t m,
                          int64_t row_base, float* d_out, void* stream);
 
+/* ---- exact brute force (float32, no tree) ----------------------------------
+ * BruteForceSearcher<float> (scann/brute_force/brute_force.cc) behind
+ * score_brute_force(): a handle of its own, nothing of smx_index is shared.
+ * The dataset is copied to the device; besides it and one float per row (the
+ * squared norms, squared L2 only) no device buffer grows with
+ * num_datapoints: the [nq][N] score matrix is never materialised (rows are
+ * scored in passes whose survivors go to a per-query candidate buffer; see
+ * scann_amd/csrc/smx_brute_force.hip).
+ *  - Distances in the internal convention (-dot; smaller is better), results
+ *    sorted by (distance, row id), padded with id 0 / NaN; out_count =
+ *    min(final_nn, num_datapoints) (may be NULL).
+ *  - final_nn in [1, 256]; a larger value is SMX_INVALID_ARGUMENT.
+ *  - nq == 0 returns SMX_OK and writes nothing.
+ *  - Calls on one handle are serialised by its mutex and share one
+ *    workspace: a call on another stream than the handle's previous call
+ *    waits on the host for that call first (a stream passed here must stay
+ *    valid until smx_bf_destroy). */
+typedef struct smx_bf_desc {
+  int32_t metric;           /* SMX_METRIC_*                                   */
+  int32_t dim;
+  uint32_t num_datapoints;
+  int32_t reserved;
+  const float* dataset;     /* [num_datapoints][dim], host, copied            */
+} smx_bf_desc;
+
+typedef struct smx_bf smx_bf;
+
+/* Of the last search call on the handle. */
+typedef struct smx_bf_stats {
+  int32_t passes;           /* row slabs scored (a pass + a fold launch each)  */
+  int32_t fallback_pieces;  /* pieces of passes redone for queries whose
+                               candidates overflowed their buffer             */
+  int32_t max_candidates;   /* largest per-query candidate count of a pass    */
+  int32_t reserved;
+} smx_bf_stats;
+
+int smx_bf_create(const smx_bf_desc* desc, int32_t device, smx_bf** out);
+/* Waits for the handle's own stream only. */
+int smx_bf_destroy(smx_bf* bf);
+
+/* Batched search, host buffers: BruteForceSearcher::FindNeighborsBatchedImpl
+ * -> DenseDistanceManyToManyTopK (brute_force.cc:379-393), the transposed
+ * many-to-many chain (many_to_many_impl.inc:522-560), exact top final_nn by
+ * (distance, row id).  queries [nq][dim]; out_idx / out_dist [nq][final_nn]. */
+int smx_bf_search_batched(smx_bf* bf, const float* queries, int32_t nq, int32_t dim,
+                          int32_t final_nn, uint32_t* out_idx, float* out_dist,
+                          int32_t* out_count);
+
+/* The same (brute_force.cc:379-393) with device buffers, enqueued on `stream`
+ * (NULL = the handle's own) without host synchronisation: a candidate
+ * overflow is handled on the device.  (It waits on the host only for a
+ * previous call of the handle that ran on a different stream, and when the
+ * workspace has to grow.) */
+int smx_bf_search_batched_device(smx_bf* bf, const float* d_queries, int32_t nq, int32_t dim,
+                                 int32_t final_nn, uint32_t* d_out_idx, float* d_out_dist,
+                                 int32_t* d_out_count, void* stream);
+
+/* Single query, host buffers: BruteForceSearcher::FindNeighborsImpl ->
+ * DenseDistanceOneToMany (brute_force.cc:398-418), whose accumulation order
+ * (one_to_many_symmetric.h:376-503) differs from the batched chain in the
+ * last bits, as the reference's search() differs from its search_batched(). */
+int smx_bf_search(smx_bf* bf, const float* query, int32_t dim, int32_t final_nn,
+                  uint32_t* out_idx, float* out_dist, int32_t* out_count);
+
+/* Rows of the first pass (each later pass takes four times the one before;
+ * default: the candidate capacity) and candidate keys per query (in
+ * [16, 3840]; default max(1024, 16 final_nn), at most 3840).  0 = default. */
+int smx_bf_set_tuning(smx_bf* bf, int32_t first_pass_rows, int32_t candidates_per_query);
+/* Waits for the handle's last call. */
+int smx_bf_get_stats(const smx_bf* bf, smx_bf_stats* out);
+
 /* ---- diagnostics ---------------------------------------------------------- */
 /* 0: off; 1: per-call stage timings (synchronous calls); 2: scan-launch
  * durations of the calls in flight (see smx_timings). */

@@ -13,6 +13,7 @@ import os
 
 import numpy as np
 
+from .brute_force import BruteForceDesc
 from .index import IndexDesc
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -42,6 +43,11 @@ class Timings(ctypes.Structure):
 
     def as_dict(self):
         return {name: getattr(self, name) for name, _ in self._fields_}
+
+
+class BruteForceStats(ctypes.Structure):
+    _fields_ = [("passes", ctypes.c_int32), ("fallback_pieces", ctypes.c_int32),
+                ("max_candidates", ctypes.c_int32), ("reserved", ctypes.c_int32)]
 
 
 # name -> (restype, argtypes); must cover every function of include/scann_mi355x.h
@@ -82,6 +88,13 @@ SIGNATURES = {
                                          _vp]),
     "smx_gather_residuals": (ctypes.c_int, [_vp, _i32, _vp, _vp, _vp, ctypes.c_int64,
                                             ctypes.c_int64, _vp, _vp]),
+    "smx_bf_create": (ctypes.c_int, [ctypes.POINTER(BruteForceDesc), _i32, ctypes.POINTER(_vp)]),
+    "smx_bf_destroy": (ctypes.c_int, [_vp]),
+    "smx_bf_search_batched": (ctypes.c_int, [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp]),
+    "smx_bf_search_batched_device": (ctypes.c_int, [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "smx_bf_search": (ctypes.c_int, [_vp, _vp, _i32, _i32, _vp, _vp, _vp]),
+    "smx_bf_set_tuning": (ctypes.c_int, [_vp, _i32, _i32]),
+    "smx_bf_get_stats": (ctypes.c_int, [_vp, ctypes.POINTER(BruteForceStats)]),
     "smx_last_error": (ctypes.c_char_p, []),
     "smx_version": (ctypes.c_char_p, []),
 }
@@ -342,3 +355,72 @@ class NativeIndex:
                    scan_variant: int = 0, chunk_tiles: int = 0):
         check(self.lib.smx_set_tuning(self.h, int(candidates_per_query), int(seed_leaves),
                                       int(scan_variant), int(chunk_tiles)), "smx_set_tuning")
+
+
+class NativeBruteForce:
+    """Owns one smx_bf handle (the device-resident dataset of the exact
+    brute-force searcher).  Distances are in the internal convention (-dot)."""
+
+    def __init__(self, index, device: int = 0):
+        self.lib = load()
+        self.index = index
+        self.dim = index.dim
+        desc = index.desc()
+        h = _vp()
+        check(self.lib.smx_bf_create(ctypes.byref(desc), device, ctypes.byref(h)), "smx_bf_create")
+        self.h = h
+
+    def close(self):
+        if getattr(self, "h", None) is not None and self.h.value:
+            self.lib.smx_bf_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def search_batched(self, queries, final_nn):
+        q = _c(queries, np.float32)
+        if q.ndim != 2:
+            raise ValueError("Queries must be in two-dimensional array")
+        nq = q.shape[0]
+        idx = np.zeros((nq, final_nn), np.uint32)
+        dist = np.zeros((nq, final_nn), np.float32)
+        cnt = np.zeros(nq, np.int32)
+        check(self.lib.smx_bf_search_batched(self.h, q.ctypes.data, nq, q.shape[1], int(final_nn),
+                                             idx.ctypes.data, dist.ctypes.data, cnt.ctypes.data),
+              "Error during search")
+        return idx, dist, cnt
+
+    def search(self, query, final_nn):
+        """One query through the one-to-many numerics (smx_bf_search)."""
+        q = _c(query, np.float32)
+        if q.ndim != 1:
+            raise ValueError("Query must be one-dimensional")
+        idx = np.zeros(final_nn, np.uint32)
+        dist = np.zeros(final_nn, np.float32)
+        cnt = np.zeros(1, np.int32)
+        check(self.lib.smx_bf_search(self.h, q.ctypes.data, q.shape[0], int(final_nn),
+                                     idx.ctypes.data, dist.ctypes.data, cnt.ctypes.data),
+              "Error during search")
+        return idx, dist, int(cnt[0])
+
+    def search_batched_device(self, q_ptr, nq, final_nn, out_idx_ptr, out_dist_ptr,
+                              out_count_ptr=None, stream=None):
+        check(self.lib.smx_bf_search_batched_device(self.h, q_ptr, int(nq), self.dim, int(final_nn),
+                                                    out_idx_ptr, out_dist_ptr, out_count_ptr,
+                                                    _current_stream(stream)),
+              "Error during search")
+
+    def set_tuning(self, first_pass_rows: int = 0, candidates_per_query: int = 0):
+        check(self.lib.smx_bf_set_tuning(self.h, int(first_pass_rows), int(candidates_per_query)),
+              "smx_bf_set_tuning")
+
+    def stats(self):
+        """passes / fallback_pieces / max_candidates of the last call."""
+        t = BruteForceStats()
+        check(self.lib.smx_bf_get_stats(self.h, ctypes.byref(t)), "smx_bf_get_stats")
+        return dict(passes=t.passes, fallback_pieces=t.fallback_pieces,
+                    max_candidates=t.max_candidates)

@@ -49,7 +49,9 @@ from typing import Any, Dict, List, Optional, Tuple
 
 import numpy as np
 
-from .config import SearchConfig, parse_text_proto, search_config_from_tree
+from .brute_force import BruteForceIndex
+from .config import (BruteForceConfig, SearchConfig, brute_force_config_from_tree, is_brute_force,
+                     parse_text_proto, search_config_from_tree)
 from .index import METRIC_NAMES, TreeAHIndex
 
 # --------------------------------------------------------------------------
@@ -682,6 +684,52 @@ def load_artifacts(artifacts_dir: str, assets_pbtxt: Optional[str] = None
         dataset=dataset if cfg.has_reordering else None,
         spilling_overretrieve_factor=cfg.overretrieve_factor if soar else 1.0)
     return index, tree, cfg
+
+
+def is_brute_force_artifacts(artifacts_dir: str) -> bool:
+    """Whether the directory's scann_config.pb asks for the brute-force
+    searcher (the dispatch in front of load_artifacts)."""
+    with open(os.path.join(artifacts_dir, "scann_config.pb"), "rb") as f:
+        return is_brute_force(decode_message(f.read(), "ScannConfig"))
+
+
+def load_brute_force_artifacts(artifacts_dir: str, assets_pbtxt: Optional[str] = None
+                               ) -> Tuple[BruteForceIndex, Dict[str, List[Any]], BruteForceConfig]:
+    """ScannInterface::LoadArtifacts (scann.cc:105-264) for a brute-force
+    searcher: the config and the float dataset."""
+    with open(os.path.join(artifacts_dir, "scann_config.pb"), "rb") as f:
+        tree = decode_message(f.read(), "ScannConfig")
+    cfg = brute_force_config_from_tree(tree)
+    if assets_pbtxt is None:
+        with open(os.path.join(artifacts_dir, "scann_assets.pbtxt")) as f:
+            assets_pbtxt = f.read()
+    assets = parse_assets(assets_pbtxt, artifacts_dir)
+    if "DATASET_NPY" not in assets:
+        raise ValueError("brute-force artifacts need a DATASET_NPY asset")
+    dataset = np.load(assets["DATASET_NPY"], allow_pickle=False)
+    if dataset.dtype != np.float32 or dataset.ndim != 2:
+        raise ValueError("dataset.npy must be float32 [N][dim]")
+    return BruteForceIndex(dataset, METRIC_NAMES[cfg.metric]), tree, cfg
+
+
+def save_brute_force_artifacts(index: BruteForceIndex, config_text: str, path: str,
+                               relative_path: bool = False) -> str:
+    """ScannInterface::Serialize (scann.cc:504-601) for a brute-force
+    searcher: scann_config.pb, dataset.npy (DATASET_NPY) and
+    scann_assets.pbtxt; returns the assets text."""
+    tree = parse_text_proto(config_text)
+    brute_force_config_from_tree(tree)
+    os.makedirs(path, exist_ok=True)
+    with open(os.path.join(path, "scann_config.pb"), "wb") as f:
+        f.write(encode_message(tree, "ScannConfig"))
+    full = os.path.join(path, "dataset.npy")
+    np.save(full, index.dataset)
+    text = format_message({"assets": [{"asset_type": ["DATASET_NPY"],
+                                       "asset_path": ["dataset.npy" if relative_path else full]}]},
+                          "ScannAssets")
+    with open(os.path.join(path, "scann_assets.pbtxt"), "w") as f:
+        f.write(text)
+    return text
 
 
 def save_artifacts(index: TreeAHIndex, config_text: str, path: str,

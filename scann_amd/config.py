@@ -6,6 +6,8 @@ strict instead: a malformed config raises ValueError.
 
 Only the fields the tree-AH LUT16 query path needs are interpreted
 (``SearchConfig`` below); everything else is kept in the tree and ignored.
+A config with a ``brute_force`` stanza is read by ``BruteForceConfig``'s
+readers instead (callers dispatch on ``is_brute_force`` first).
 """
 from __future__ import annotations
 
@@ -187,3 +189,44 @@ def search_config_from_tree(tree: Dict[str, List[Any]]) -> SearchConfig:
         overretrieve_factor=float(_get(spill, "overretrieve_factor", default=2.0)) if spill else 2.0,
         noise_shaping_threshold=_noise_shaping(ah),
         raw=tree)
+
+
+@dataclasses.dataclass
+class BruteForceConfig:
+    """What the exact float32 brute-force searcher needs from a ScannConfig
+    (ScannBuilder.score_brute_force() without a tree)."""
+
+    num_neighbors: int
+    metric: str                       # "dot_product" | "squared_l2"
+    raw: Optional[Dict[str, List[Any]]] = dataclasses.field(default=None, compare=False, repr=False)
+
+
+def is_brute_force(tree: Dict[str, List[Any]]) -> bool:
+    """Whether a parsed config takes the brute-force searcher (the dispatch in
+    front of search_config_from_tree, which rejects such configs)."""
+    return "brute_force" in tree
+
+
+def brute_force_config_from_text(text: str) -> BruteForceConfig:
+    return brute_force_config_from_tree(parse_text_proto(text))
+
+
+def brute_force_config_from_tree(tree: Dict[str, List[Any]]) -> BruteForceConfig:
+    nn = _get(tree, "num_neighbors")
+    if nn is None:
+        raise ValueError("config has no num_neighbors")
+    dist = _get(tree, "distance_measure", "distance_measure")
+    if dist not in _DISTANCES:
+        raise ValueError(f"unsupported distance_measure {dist!r} (dot product or squared L2)")
+    if "brute_force" not in tree:
+        raise ValueError("config has no brute_force stanza")
+    if "partitioning" in tree:
+        raise ValueError("a tree over brute-force leaves is not supported (score_brute_force "
+                         "without tree only)")
+    if "hash" in tree:
+        raise ValueError("brute_force and hash in one config")
+    if _get(tree, "brute_force", "fixed_point", "enabled"):
+        raise ValueError("int8 brute force (quantize=True) is not supported (float32 only)")
+    if _get(tree, "brute_force", "bfloat16", "enabled"):
+        raise ValueError("bfloat16 brute force is not supported (float32 only)")
+    return BruteForceConfig(num_neighbors=int(nn), metric=_DISTANCES[dist], raw=tree)

@@ -7,6 +7,8 @@
 #include <hip/hip_ext.h>
 #include <stdint.h>
 
+#include <string>
+
 namespace smx {
 
 // Query-tile width of the LUT16 scan: one MFMA i32_32x32x32_i8 covers 32
@@ -414,6 +416,8 @@ hipError_t SetPhaseStamps(unsigned long long* p);
 // Debug build only (-DSMX_DEBUG_CHECKS): index-check violations counted on
 // the device since the last call (reset to 0); always 0 in the product build.
 hipError_t TakeCheckFailures(unsigned int* out);
+// Sets the calling thread's smx_last_error() message; returns `code`.
+int SetLastError(int code, const std::string& msg);
 hipError_t LaunchFill64(uint64_t* p, uint64_t v, size_t n, hipStream_t s);
 // row_of[members[m]] = m for every member slot m (row_of pre-filled).
 hipError_t LaunchRowOf(const uint32_t* members, uint64_t m, uint32_t* row_of, hipStream_t s);

@@ -16,6 +16,7 @@
 // and holds the config defaults ScannInterface resolves -1 arguments against
 // (scann.cc:384-430).  Index construction (training, asset parsing) stays in
 // Python; everything a search call does on the host is here.
+// BruteForceCore is the same surface over the brute-force handle (smx_bf).
 #include <pybind11/numpy.h>
 #include <pybind11/pybind11.h>
 
@@ -145,6 +146,92 @@ class ScannNumpyCore {
   size_t size_ = 0;
 };
 
+// The same surface over the exact brute-force searcher (smx_bf_*,
+// score_brute_force() without a tree): BruteForceSearcher<float> behind
+// ScannNumpy.  pre_reorder_nn and leaves are accepted and ignored (there is
+// no reordering stage and no tree).
+class BruteForceCore {
+ public:
+  // desc_address: the address of a filled smx_bf_desc (its dataset is copied
+  // to the device by smx_bf_create).
+  BruteForceCore(uintptr_t desc_address, int device, int num_neighbors, bool dot_product)
+      : num_neighbors_(num_neighbors), multiplier_(dot_product ? -1.0f : 1.0f) {
+    if (desc_address == 0) throw std::invalid_argument("null dataset description");
+    const auto* desc = reinterpret_cast<const smx_bf_desc*>(desc_address);
+    RuntimeErrorIfNotOk("Failed to create the searcher: ", smx_bf_create(desc, device, &h_));
+    dim_ = desc->dim;
+    size_ = desc->num_datapoints;
+  }
+  ~BruteForceCore() {
+    if (h_) smx_bf_destroy(h_);
+  }
+  BruteForceCore(const BruteForceCore&) = delete;
+  BruteForceCore& operator=(const BruteForceCore&) = delete;
+
+  std::pair<py::array_t<uint32_t>, py::array_t<float>> Search(const np_row_major_arr<float>& query,
+                                                              int final_nn, int pre_reorder_nn,
+                                                              int leaves) {
+    (void)pre_reorder_nn;
+    (void)leaves;
+    if (query.ndim() != 1) throw std::invalid_argument("Query must be one-dimensional");
+    const int k = final_nn > 0 ? final_nn : num_neighbors_;
+    py::array_t<uint32_t> idx(k);
+    py::array_t<float> dist(k);
+    int32_t count = 0;
+    int rc;
+    {
+      py::gil_scoped_release release;
+      rc = smx_bf_search(h_, query.data(), int32_t(query.size()), k, idx.mutable_data(),
+                         dist.mutable_data(), &count);
+    }
+    RuntimeErrorIfNotOk("Error during search: ", rc);
+    py::array_t<uint32_t> out_idx(count);
+    py::array_t<float> out_dist(count);
+    for (int32_t i = 0; i < count; ++i) {
+      out_idx.mutable_data()[i] = idx.data()[i];
+      out_dist.mutable_data()[i] = dist.data()[i] * multiplier_;
+    }
+    return {out_idx, out_dist};
+  }
+
+  std::pair<py::array_t<uint32_t>, py::array_t<float>> SearchBatched(
+      const np_row_major_arr<float>& queries, int final_nn, int pre_reorder_nn, int leaves,
+      bool parallel, int batch_size) {
+    (void)pre_reorder_nn;
+    (void)leaves;
+    (void)parallel;
+    (void)batch_size;
+    if (queries.ndim() != 2)
+      throw std::invalid_argument("Queries must be in two-dimensional array");
+    const int k = final_nn > 0 ? final_nn : num_neighbors_;
+    const py::ssize_t nq = queries.shape(0);
+    py::array_t<uint32_t> idx({nq, py::ssize_t(k)});
+    py::array_t<float> dist({nq, py::ssize_t(k)});
+    int rc;
+    {
+      py::gil_scoped_release release;
+      rc = smx_bf_search_batched(h_, queries.data(), int32_t(nq), int32_t(queries.shape(1)), k,
+                                 idx.mutable_data(), dist.mutable_data(), nullptr);
+      if (rc == SMX_OK && multiplier_ != 1.0f) {
+        float* d = dist.mutable_data();
+        for (py::ssize_t i = 0; i < nq * k; ++i) d[i] *= multiplier_;   // NaN pads stay NaN
+      }
+    }
+    RuntimeErrorIfNotOk("Error during search: ", rc);
+    return {idx, dist};
+  }
+
+  size_t Size() const { return size_; }
+  int Dim() const { return dim_; }
+
+ private:
+  smx_bf* h_ = nullptr;
+  int num_neighbors_;
+  float multiplier_;
+  int dim_ = 0;
+  size_t size_ = 0;
+};
+
 }  // namespace
 
 PYBIND11_MODULE(_smx_pybind, m) {
@@ -160,4 +247,14 @@ PYBIND11_MODULE(_smx_pybind, m) {
            py::arg("parallel") = false, py::arg("batch_size") = 256)
       .def("size", &ScannNumpyCore::Size)
       .def("dim", &ScannNumpyCore::Dim);
+  py::class_<BruteForceCore>(m, "BruteForceCore")
+      .def(py::init<uintptr_t, int, int, bool>(), py::arg("desc_address"), py::arg("device"),
+           py::arg("num_neighbors"), py::arg("dot_product"))
+      .def("search", &BruteForceCore::Search, py::arg("query"), py::arg("final_nn") = -1,
+           py::arg("pre_reorder_nn") = -1, py::arg("leaves") = -1)
+      .def("search_batched", &BruteForceCore::SearchBatched, py::arg("queries"),
+           py::arg("final_nn") = -1, py::arg("pre_reorder_nn") = -1, py::arg("leaves") = -1,
+           py::arg("parallel") = false, py::arg("batch_size") = 256)
+      .def("size", &BruteForceCore::Size)
+      .def("dim", &BruteForceCore::Dim);
 }

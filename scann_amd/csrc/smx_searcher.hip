@@ -37,6 +37,14 @@ int Fail(int code, const std::string& msg) {
   return code;
 }
 
+}  // namespace
+
+// The calling thread's smx_last_error() message, for the other translation
+// units behind the C ABI (smx_brute_force.hip).
+int smx::SetLastError(int code, const std::string& msg) { return Fail(code, msg); }
+
+namespace {
+
 #define SMX_HIP(expr)                                                              \
   do {                                                                             \
     hipError_t _e = (expr);                                                        \

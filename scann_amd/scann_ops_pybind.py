@@ -5,6 +5,11 @@
         num_leaves=1000, num_leaves_to_search=100).score_ah(2).reorder(100).build()
     neighbors, distances = searcher.search_batched(queries)
 
+``score_brute_force()`` without ``tree()`` builds the exact float32
+brute-force searcher (a fused distance GEMM + top-k on the GPU); it
+serializes as scann_config.pb + dataset.npy + scann_assets.pbtxt and
+``load_searcher`` brings it back.
+
 Out of scope for this tier: online mutation (upsert,
 delete, rebalance, reserve), health stats and autopilot; they raise
 NotImplementedError rather than silently doing nothing.

@@ -19,6 +19,10 @@ tree-AH LUT16 path:
   the reference's "Error during search: " prefix (scann_npy.cc:41-55).
   The search calls run in C++ (``ScannNumpyCore``, scann_amd/csrc/
   smx_pybind.cc, a pybind11 module over the C ABI).
+* A config with a ``brute_force`` stanza (``score_brute_force()`` without a
+  tree) builds the exact float32 brute-force searcher instead
+  (``BruteForceCore`` over smx_bf_*; scann_amd/csrc/smx_brute_force.hip):
+  ``pre_reorder_nn`` and ``leaves`` are accepted and ignored.
 """
 from __future__ import annotations
 
@@ -29,7 +33,8 @@ import os
 import numpy as np
 
 from . import _native, assets
-from .config import SearchConfig, search_config_from_text
+from .config import (SearchConfig, brute_force_config_from_text, is_brute_force, parse_text_proto,
+                     search_config_from_text)
 from .index import METRIC_NAMES, TreeAHIndex
 
 
@@ -48,6 +53,23 @@ def _own_format(directory: str) -> bool:
 class ScannNumpy:
     def __init__(self, db_or_dir, config: str, training_threads: int = 0, device: int = 0,
                  seed: int = 0):
+        self._brute_force = False
+        if isinstance(db_or_dir, str) and not _own_format(db_or_dir) and \
+                assets.is_brute_force_artifacts(db_or_dir):
+            index, tree, self._cfg = assets.load_brute_force_artifacts(db_or_dir, config or None)
+            self._init_brute_force(index, assets.config_text(tree), device)
+            return
+        if not isinstance(db_or_dir, str) and is_brute_force(parse_text_proto(config)):
+            # score_brute_force() without a tree: the exact float32 searcher
+            # (dispatched before search_config_from_text, the tree-AH reader)
+            self._cfg = brute_force_config_from_text(config)
+            from .brute_force import BruteForceIndex
+            db = np.asarray(db_or_dir)
+            if db.ndim != 2:
+                raise ValueError("dataset must be two-dimensional")
+            self._init_brute_force(BruteForceIndex(db, METRIC_NAMES[self._cfg.metric]), config,
+                                   device)
+            return
         if isinstance(db_or_dir, str) and _own_format(db_or_dir):
             # a directory saved by TreeAHIndex.save (this package's own
             # format) with the config text beside it in scann_config.pbtxt
@@ -89,6 +111,17 @@ class ScannNumpy:
             cfg.reorder_num_neighbors if cfg.has_reordering else cfg.num_neighbors,
             cfg.leaves_to_search, cfg.has_reordering, cfg.metric == "dot_product")
 
+    def _init_brute_force(self, index, config_text: str, device: int) -> None:
+        self._brute_force = True
+        self._config_text = config_text
+        self._index = index
+        self._device = device
+        self._native = None
+        desc = index.desc()
+        self._core = _native.load_pybind().BruteForceCore(
+            ctypes.addressof(desc), device, self._cfg.num_neighbors,
+            self._cfg.metric == "dot_product")
+
     # -- parameter resolution (ScannInterface::GetSearchParameters[Batched]) --
     def _resolve(self, final_nn: int, pre_reorder_nn: int, leaves: int):
         cfg = self._cfg
@@ -116,6 +149,10 @@ class ScannNumpy:
 
     def serialize(self, path: str, relative_path: bool = False) -> None:
         try:
+            if self._brute_force:
+                assets.save_brute_force_artifacts(self._index, self._config_text, path,
+                                                  relative_path)
+                return
             assets.save_artifacts(self._index, self._config_text, path, relative_path)
         except (OSError, ValueError) as e:
             raise RuntimeError(f"Failed to extract SingleMachineFactoryOptions: {e}") from None
@@ -129,13 +166,15 @@ class ScannNumpy:
     def set_num_threads(self, num_threads: int) -> None:
         del num_threads  # host threads do not drive the GPU pipeline
 
-    def native(self) -> _native.NativeIndex:
+    def native(self):
         """A ctypes handle on its own device copy of the index (stage entry
-        points, tuning); created on first use."""
+        points, tuning); created on first use.  A NativeBruteForce for a
+        brute-force searcher."""
         if self._native is None:
-            self._native = _native.NativeIndex(self._index, device=self._device)
+            cls = _native.NativeBruteForce if self._brute_force else _native.NativeIndex
+            self._native = cls(self._index, device=self._device)
         return self._native
 
     @property
-    def index(self) -> TreeAHIndex:
+    def index(self):
         return self._index
