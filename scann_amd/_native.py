@@ -176,7 +176,10 @@ def _current_stream(stream):
     """The HIP stream a device entry point runs on: the caller's, else torch's
     current stream when torch is in use (the device entry points return with
     the work enqueued, so results are ordered with the caller's own reads and
-    writes of those buffers), else the library's own stream (None)."""
+    writes of those buffers), else the library's own stream (None).  torch's
+    default stream has the handle 0, which the C ABI reads as the library's
+    own stream too: that one is not ordered with the default stream, so a
+    caller on the default stream synchronises the device around the call."""
     if stream is not None:
         return stream
     torch = sys.modules.get("torch")
